@@ -14,13 +14,19 @@ one pack or unpack of P payload bytes moves 2P (read P + write P; SURVEY
 8(d)). N > 1 (torchrun): every rank packs its own object on its own GPU, no
 collective on the data path (weak scaling, replicas).
 
-The same line carries "halo": the 3D halo exchange of config 4 (512^3 grid,
+A plain run does that and no more: set up, warm up, time --steps steps,
+write the last step's outputs when --dump-outputs DIR is given, print the
+line. Everything below is evidence beside the metric and runs with --full
+only, after the headline (as do the parity check of the timed buffers, the
+device-to-device copy calibration and the detail record).
+
+With --full the line also carries "halo": the 3D halo exchange of config 4 (512^3 grid,
 8 quantities of 8 B, radius 3, 26 neighbours, periodic, 3 substeps per
 iteration) run through MPI_Isend/MPI_Irecv/MPI_Wait on the same ranks
 (strong scaling of the fixed grid), with its xGMI roofline. Under torchrun
 the ranks are wired into one MPI job by tempi_amd.pmi.
 
-At N > 1 the line also carries "pingpong" (config 3, ranks 0 <-> 1),
+At N > 1 the --full line also carries "pingpong" (config 3, ranks 0 <-> 1),
 "pingpong_1d" (the contiguous ping-pong, all pairs),
 "alltoallv" (config 5, all ranks) and "nbr_alltoallv" (config 5's
 neighbourhood form), each with its xGMI fraction.
@@ -52,6 +58,13 @@ def parse():
     p.add_argument("--rows", type=int, default=2 * 1024 * 1024)
     p.add_argument("--pitch", type=int, default=1024)
     p.add_argument("--block", type=int, default=512)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, run every other section of the line (parity check, sweep, halo, counter "
+                        "traffic, CPU baselines, the N > 1 sections) and write the detail record; a plain run sets "
+                        "up, warms up, times --steps steps and prints the headline line only")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step computed (the packed buffer and the "
+                        "unpacked object; a fixed, seeded sample of each when large) as DIR/<name>.npy, float32")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=8.0)
     p.add_argument("--no-traffic", action="store_true",
@@ -531,6 +544,39 @@ def halo_traffic(args):
     return out["FETCH_SIZE"] * 2.0, out["WRITE_SIZE"]
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each dumped array: 16 MiB as float32
+DUMP_SEED = 20240229
+
+
+def dump_indices(n):
+    """The element indices --dump-outputs keeps of an array of n elements:
+    None (all of it) up to DUMP_SAMPLE elements, else DUMP_SAMPLE indices --
+    its first and last 64 Ki elements, and the rest drawn from a fixed seed
+    (the same for every run of the same size, in ascending order)."""
+    import numpy as np
+
+    if n <= DUMP_SAMPLE:
+        return None
+    edge = 1 << 16
+    rnd = np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE - 2 * edge, dtype=np.int64)
+    return np.concatenate([np.arange(edge), np.sort(rnd), np.arange(n - edge, n)]).astype(np.int64)
+
+
+def dump_outputs(outdir, torch, arrays):
+    """--dump-outputs: every array of `arrays` (device tensors, what the timed
+    step's caller receives) as outdir/<name>.npy in float32, a large one at
+    dump_indices() only, so that two builds are compared element for element."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        flat = a.reshape(-1)
+        idx = dump_indices(flat.numel())
+        if idx is not None:
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(outdir, name + ".npy"), flat.cpu().numpy().astype(np.float32))
+
+
 def headline(args, mpi, torch, rank, world, pg, dev):
     rows, pitch, block = args.rows, args.pitch, args.block
     payload = rows * block
@@ -546,12 +592,13 @@ def headline(args, mpi, torch, rank, world, pg, dev):
 
     for _ in range(args.warmup):
         step()
-    # parity of what is being timed (exact, via strided views)
     torch.cuda.synchronize()
-    ok = torch.equal(packed.view(rows, block), src.view(rows, pitch)[:, :block]) and torch.equal(
-        dst.view(rows, pitch)[:, :block], src.view(rows, pitch)[:, :block])
-    if not ok:
-        raise SystemExit("bench parity check failed: packed bytes differ from the strided source")
+    if args.full and args.warmup > 0:
+        # parity of what is being timed (exact, via strided views)
+        ok = torch.equal(packed.view(rows, block), src.view(rows, pitch)[:, :block]) and torch.equal(
+            dst.view(rows, pitch)[:, :block], src.view(rows, pitch)[:, :block])
+        if not ok:
+            raise SystemExit("bench parity check failed: packed bytes differ from the strided source")
 
     mpi.reset_counters()
     mpi.set_kernel_profiling(True)
@@ -570,10 +617,13 @@ def headline(args, mpi, torch, rank, world, pg, dev):
     total_alg = allreduce_sum(pg, alg_step * args.steps)
     value = total_alg / el_max / 1e9
     mpi.Type_free(t)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, {"packed": packed, "unpacked": dst})
 
     # the box's achievable HBM rate for the same bytes: a device-to-device
-    # copy of the packed size (read + write, SURVEY 8(d) "calibrated peak")
-    cal = calibrate_copy(torch, packed, dst, payload)
+    # copy of the packed size (read + write, SURVEY 8(d) "calibrated peak");
+    # a run of its own, so with --full only
+    cal = calibrate_copy(torch, packed, dst, payload) if args.full else None
     launches = kt["packs"] + kt["unpacks"]
     avg_ms = (kt["pack_ms"] + kt["unpack_ms"]) / max(launches, 1)
     alg_launch = 2.0 * payload
@@ -618,7 +668,7 @@ def headline(args, mpi, torch, rank, world, pg, dev):
             # pack kernel itself, so not a ceiling)
             "achievable_peak": HBM_ACHIEVABLE_GBS,
             "frac_achievable": round(achieved / HBM_ACHIEVABLE_GBS, 4),
-            "d2d_copy_GBps": round(cal, 1),
+            "d2d_copy_GBps": round(cal, 1) if cal is not None else None,
             "calibration": ("achievable_peak: MI355X_MICROARCH.md HBM section (~6.3 TB/s streaming); d2d_copy_GBps: "
                             "torch copy_ (hipMemcpyAsync D2D) of the packed size, 10 launches, HIP events"),
         },
@@ -1438,6 +1488,11 @@ def main():
             return
         rec = headline(args, mpi, torch, rank, world, pg, dev)
         if args.inner:
+            return
+        if not args.full:  # a plain run: the headline alone (the detail record only when it was named)
+            if rank == 0:
+                print(json.dumps(compact_line(rec, world > max(torch.cuda.device_count(), 1),
+                                              write_detail(rec, world) if DETAIL_NAME else None)), flush=True)
             return
         torch.cuda.empty_cache()
         shared_gpu = world > max(torch.cuda.device_count(), 1)

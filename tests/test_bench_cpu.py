@@ -96,6 +96,40 @@ def test_section_deadline_prints_the_line_so_far():
     assert line["incomplete"] == {"section": "halo", "deadline_s": 0.5}
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless asked for, --steps / --warmup are taken as given"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small array whole, a large one at the same seeded
+    indices every time (its two ends included), float32 either way"""
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1 << 18)
+    small = (torch.arange(1000, dtype=torch.int64) & 0xFF).to(torch.uint8)
+    n = (1 << 20) + 37
+    large = (torch.arange(n, dtype=torch.int64) % 251).to(torch.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, {"small": small, "large": large})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy().astype(np.float32))
+    la, lb = np.load(tmp_path / "a" / "large.npy"), np.load(tmp_path / "b" / "large.npy")
+    assert la.dtype == np.float32 and la.shape == (1 << 18,) and np.array_equal(la, lb)
+    edge = 1 << 16
+    full = large.numpy().astype(np.float32)
+    assert np.array_equal(la[:edge], full[:edge]) and np.array_equal(la[-edge:], full[-edge:])
+    # the sample is of `large` itself: another array of the same size differs in it
+    bench.dump_outputs(str(tmp_path / "c"), torch, {"large": large + 1})
+    assert not np.array_equal(np.load(tmp_path / "c" / "large.npy"), la)
+
+
 def _brute_classes(bl, st, n, first):
     """line classes of n rows, byte by byte (small cases only)"""
     lines = {}

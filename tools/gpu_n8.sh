@@ -1,7 +1,7 @@
 #!/bin/bash
 # The driver's 8-GPU bench command shape, rehearsed with 8 ranks sharing this
 # box's one GPU: torchrun --nproc-per-node 8 bench.py
-# --gpus 8 with the default steps / warmup. Prints the wall time, the line's
+# --full --gpus 8 with the default steps / warmup. Prints the wall time, the line's
 # size and whether it parses; line in gpurun_out/tr_8.json, full record in
 # gpurun_out/bench_detail_n8.json, stderr in gpurun_out/tr_8.err.
 cd "$(dirname "$0")/.."
@@ -10,7 +10,7 @@ O=gpurun_out; mkdir -p $O
 N=${N:-8}
 t0=$(date +%s.%N)
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port 29733 bench.py --gpus $N > $O/tr_$N.json 2> $O/tr_$N.err
+  --master-port 29733 bench.py --full --gpus $N > $O/tr_$N.json 2> $O/tr_$N.err
 rc=$?
 t1=$(date +%s.%N)
 echo "N=$N rc=$rc wall_s=$(python3 -c "print(round($t1-$t0,1))")"

@@ -1,16 +1,19 @@
 #!/bin/bash
-# The driver's multi-GPU bench command at N=2 and N=4 (ranks sharing this
-# box's GPU): torchrun, every section of the line. JSON in gpurun_out/tr_N.json.
+# The multi-GPU bench command at N=2 and N=4 (ranks sharing one GPU):
+# torchrun, every section of the line (--full). JSON in $OUT_DIR/tr_N.json
+# (default bench_out/).
 cd "$(dirname "$0")/.."
+O=${OUT_DIR:-bench_out}
+mkdir -p "$O"
 P=29611
 for n in ${NS:-2 4}; do
   P=$((P + 1))
   timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port $P bench.py --gpus $n --steps 5 --warmup 2 > gpurun_out/tr_$n.json 2> gpurun_out/tr_$n.err
+    --master-port $P bench.py --full --gpus $n --steps 5 --warmup 2 > "$O/tr_$n.json" 2> "$O/tr_$n.err"
   rc=$?
   echo "N=$n rc=$rc"
   [ $rc -eq 0 ] || exit $rc
-  python3 - gpurun_out/tr_$n.json <<'PY'
+  python3 - "$O/tr_$n.json" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 h = d["halo"]
