@@ -79,8 +79,16 @@ $(LIB)/%: apps/%.cpp $(LIB)/libtempi.so
 oracle:
 	$(MAKE) -s -C oracle all
 
+# the segment-list packer's pure core under the host sanitizers (plain g++:
+# no MPI, no HIP, nothing preloaded)
+selftest: tools/seglist_selftest.cpp tempi_amd/csrc/core/seglist_core.hpp
+	@mkdir -p build
+	g++ -std=c++17 -g -O1 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -Itempi_amd/csrc/core tools/seglist_selftest.cpp -o build/seglist_selftest
+	build/seglist_selftest
+
 clean:
 	rm -rf build $(LIB)/*.so $(APPS)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean
+.PHONY: all oracle clean selftest

@@ -58,9 +58,30 @@ typedef struct tempi_counters_t {
   /* payload bytes of device-object sends by route: IPC (IPC COPY included,
      and counted again on its own), ONESHOT, STAGED, DEVICE, DIRECT (this process) */
   uint64_t bytes_ipc, bytes_ipc_copy, bytes_oneshot, bytes_staged, bytes_device, bytes_direct;
+  /* MPI_Pack / MPI_Unpack of irregular types done by the segment-list kernels
+     (TEMPI_IRREGULAR; counted in packs / unpacks as well) */
+  uint64_t irregular_packs, irregular_unpacks;
 } tempi_counters_t;
 void tempi_get_counters(tempi_counters_t *out);
 void tempi_reset_counters(void);
+
+/* Irregular datatypes (ragged or irregular (h)indexed / indexed_block, struct
+   of several types, and types built over them) on the GPU: opt-in, off unless
+   TEMPI_IRREGULAR is set at MPI_Init. While on, MPI_Type_commit flattens such
+   a type into a segment list of at most `max_segs` merged runs per element
+   (default 1 << 20; max_segs <= 0 keeps the current cap), and MPI_Pack /
+   MPI_Unpack of a flattened type between GPU-reachable buffers run the
+   segment-list kernels. Types committed while it is off stay with the library
+   for their lifetime; turning it off sends later calls on flattened types to
+   the library too. tempi_type_describe keeps valid = 0 for these types.
+   Returns the previous on / off state. */
+int tempi_irregular_config(int on, int64_t max_segs);
+/* the segment list of a committed type: byte runs (disp, len) of one element
+   in MPI type-map order, merged only where a run starts exactly at the end of
+   the one before. Returns the run count and writes up to `cap` runs (disp /
+   len may be NULL when cap is 0) and the extent; -1 when the type has none
+   (strided, unknown, over the cap, committed with the feature off). */
+int64_t tempi_type_segments(int64_t datatype, int64_t *disp, int64_t *len, int64_t cap, int64_t *extent);
 
 /* Kernel timing of synchronous MPI_Pack / MPI_Unpack: when on, TEMPI
    brackets each operation's launches with HIP events on its stream and

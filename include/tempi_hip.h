@@ -155,6 +155,43 @@ int tempi_hip_copy_word_width(void *dst_first, const void *src_first, const temp
 int tempi_hip_word_width(const void *packed, const void *first,
                          const tempi_hip_desc *d);
 
+/* Irregular datatypes (ragged / irregular (h)indexed, struct of several
+   types): the type map of ONE element as `nsegs` byte runs (disp[i], len[i])
+   in MPI type-map order, len[i] > 0, displacements relative to the MPI buffer
+   address (64-bit, may be negative or out of order). The packed form of
+   `count` elements is, element after element (`extent` bytes apart), the runs
+   back to back. The reference has no packer for these (a null packer);
+   the oracle is the library's MPI_Pack. A seglist owns a device copy of the
+   table (the runs' displacements and the exclusive prefix sums of their
+   lengths) on the device that was current at creation. */
+typedef struct tempi_hip_seglist tempi_hip_seglist;
+int tempi_hip_seglist_create(tempi_hip_seglist **out, const int64_t *disp, const int64_t *len,
+                             int64_t nsegs, int64_t extent);
+int tempi_hip_seglist_destroy(tempi_hip_seglist *s);
+/* packed[0 .. count*size) <- count elements whose origin (MPI buffer address) is `origin` */
+int tempi_hip_pack_seglist(void *packed, const void *origin, const tempi_hip_seglist *s, int64_t count,
+                           void *stream);
+/* count elements at `origin` <- packed[0 .. count*size): exactly the bytes of the type map are written */
+int tempi_hip_unpack_seglist(void *origin, const void *packed, const tempi_hip_seglist *s, int64_t count,
+                             void *stream);
+/* the same plus a completion ticket (the ticket kernel queued behind the
+   work), same contract as tempi_hip_pack_ticket; *flag = NULL when nothing
+   was launched (count * size == 0) */
+int tempi_hip_pack_seglist_ticket(void *packed, const void *origin, const tempi_hip_seglist *s, int64_t count,
+                                  void *stream, const uint32_t **flag, uint32_t *ticket);
+int tempi_hip_unpack_seglist_ticket(void *origin, const void *packed, const tempi_hip_seglist *s, int64_t count,
+                                    void *stream, const uint32_t **flag, uint32_t *ticket);
+/* the word width (1,2,4,8,16) the segment-list kernels use for this call: the
+   largest that divides every disp and len, both addresses, and (count > 1)
+   the extent */
+int tempi_hip_seglist_word_width(const void *packed, const void *origin, const tempi_hip_seglist *s,
+                                 int64_t count);
+/* packed bytes one workgroup of the segment-list kernels owns (a tile), and
+   the most runs of a tile whose slice of the table is staged in LDS (a tile
+   that meets more looks its runs up in global memory) */
+int64_t tempi_hip_seglist_tile_bytes(void);
+int64_t tempi_hip_seglist_lds_runs(void);
+
 /* devices */
 int tempi_hip_device_count(int *n);
 /* a 16-byte identity of the physical GPU (the same in every process that

@@ -16,6 +16,9 @@ struct Counters {
   uint64_t lib_packs = 0, lib_unpacks = 0; // handed to the library
   // GPU packs into / unpacks from pageable host memory through a pinned slab
   uint64_t staged_packs = 0, staged_unpacks = 0;
+  // GPU packs / unpacks of irregular types by the segment-list kernels
+  // (seglist.hpp); counted in packs / unpacks too
+  uint64_t irregular_packs = 0, irregular_unpacks = 0;
   // synchronous MPI_Pack / MPI_Unpack completed by a ticket (device memory or
   // TEMPI's coherent slab written) or by hipStreamSynchronize (the
   // application's pinned host memory written)

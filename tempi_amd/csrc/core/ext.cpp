@@ -91,6 +91,31 @@ TEMPI_EXPORT void tempi_get_counters(tempi_counters_t *o) {
   o->bytes_staged = c.bytes_staged;
   o->bytes_device = c.bytes_device;
   o->bytes_direct = c.bytes_direct;
+  o->irregular_packs = c.irregular_packs;
+  o->irregular_unpacks = c.irregular_unpacks;
+}
+
+TEMPI_EXPORT int tempi_irregular_config(int on, int64_t max_segs) {
+  TEMPI_MT_ENTRY;
+  const int prev = env.irregular ? 1 : 0;
+  env.irregular = on != 0;
+  if (max_segs > 0) env.irregularMaxSegs = max_segs;
+  return prev;
+}
+
+TEMPI_EXPORT int64_t tempi_type_segments(int64_t datatype, int64_t *disp, int64_t *len, int64_t cap,
+                                         int64_t *extent) {
+  TEMPI_MT_ENTRY;
+  const TypeRecord *rec = type_lookup(MPI_Datatype(datatype));
+  if (!rec || !rec->irregular) return -1;
+  const seg::Table &t = rec->irregular->table();
+  const int64_t n = int64_t(t.disp.size());
+  for (int64_t i = 0; i < n && i < cap; ++i) {
+    if (disp) disp[i] = t.disp[size_t(i)];
+    if (len) len[i] = t.len[size_t(i)];
+  }
+  if (extent) *extent = t.extent;
+  return n;
 }
 
 TEMPI_EXPORT void tempi_reset_counters(void) {

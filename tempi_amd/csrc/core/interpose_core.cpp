@@ -406,22 +406,33 @@ TEMPI_EXPORT int MPI_Type_free(MPI_Datatype *datatype) {
 }
 
 namespace tempi {
+// the segment-list packer of a type with no strided form, when it was
+// flattened at commit and the feature is on now (tempi_irregular_config may
+// have turned it off since: then the library route, as for any other type)
+static const SegPacker *irregular_packer(const TypeRecord *rec) {
+  return rec && !rec->packer && rec->irregular && env.irregular ? rec->irregular.get() : nullptr;
+}
+
 int pack(const void *inbuf, int incount, MPI_Datatype datatype, void *outbuf, int outsize, int *position,
-         MPI_Comm comm) {
+         MPI_Comm comm, bool application) {
   if (!state.active || env.noPack || incount <= 0 || !position)
     return next.MPI_Pack(inbuf, incount, datatype, outbuf, outsize, position, comm);
   const TypeRecord *rec = type_lookup(datatype);
-  if (!rec || !rec->packer || rec->desc.size == 0)
+  const SegPacker *irr = application ? irregular_packer(rec) : nullptr;
+  if (!rec || (!rec->packer && !irr) || rec->desc.size == 0)
     return library_pack(inbuf, incount, datatype, outbuf, outsize, position, comm);
-  const char *first = static_cast<const char *>(inbuf) + rec->desc.start;
+  // the first byte the type touches: desc.start, or an irregular type's lowest
+  // displacement (its desc.start is 0). `origin` stays the MPI buffer address
+  const int64_t start = irr ? irr->table().lowest : rec->desc.start;
+  const char *first = static_cast<const char *>(inbuf) + start;
   const gpu::Ptr src = gpu::classify(first);
   if (!src.device_accessible)
     return library_pack(inbuf, incount, datatype, outbuf, outsize, position, comm);
   const gpu::Ptr dst = gpu::classify(static_cast<char *>(outbuf) + *position);
-  const int64_t bytes = rec->packer->packed_bytes(incount);
+  const int64_t bytes = irr ? irr->packed_bytes(incount) : rec->packer->packed_bytes(incount);
   if (*position < 0 || int64_t(*position) + bytes > int64_t(outsize))
     return raise_error(comm, MPI_ERR_TRUNCATE);
-  const char *origin = static_cast<const char *>(src.dptr) - rec->desc.start;
+  const char *origin = static_cast<const char *>(src.dptr) - start;
   // a GPU object packed into pageable host memory: the kernel gathers into a
   // pinned, mapped slab (as the ONESHOT sender does) and the packed bytes are
   // copied out on the host -- only the payload crosses the host link, where
@@ -434,6 +445,7 @@ int pack(const void *inbuf, int incount, MPI_Datatype datatype, void *outbuf, in
   const bool ticketOk = stage != nullptr || !dst.host_accessible;
   const int e = env.faultPack ? 1 : on_device(src.device, true, ticketOk, [&](void *s, Packer::Completion *done) {
     void *out = stage ? stage->dev : dst.dptr;
+    if (irr) return done ? irr->pack_ticket(out, origin, incount, s, done) : irr->pack_async(out, origin, incount, s);
     return done ? rec->packer->pack_ticket(out, origin, incount, s, done)
                 : rec->packer->pack_async(out, origin, incount, s);
   });
@@ -452,21 +464,23 @@ int pack(const void *inbuf, int incount, MPI_Datatype datatype, void *outbuf, in
 }
 
 int unpack(const void *inbuf, int insize, int *position, void *outbuf, int outcount, MPI_Datatype datatype,
-           MPI_Comm comm) {
+           MPI_Comm comm, bool application) {
   if (!state.active || env.noPack || outcount <= 0 || !position)
     return next.MPI_Unpack(inbuf, insize, position, outbuf, outcount, datatype, comm);
   const TypeRecord *rec = type_lookup(datatype);
-  if (!rec || !rec->packer || rec->desc.size == 0)
+  const SegPacker *irr = application ? irregular_packer(rec) : nullptr;
+  if (!rec || (!rec->packer && !irr) || rec->desc.size == 0)
     return library_unpack(inbuf, insize, position, outbuf, outcount, datatype, comm);
-  char *first = static_cast<char *>(outbuf) + rec->desc.start;
+  const int64_t start = irr ? irr->table().lowest : rec->desc.start; // (as in pack)
+  char *first = static_cast<char *>(outbuf) + start;
   const gpu::Ptr dst = gpu::classify(first);
   if (!dst.device_accessible)
     return library_unpack(inbuf, insize, position, outbuf, outcount, datatype, comm);
   const gpu::Ptr src = gpu::classify(static_cast<const char *>(inbuf) + *position);
-  const int64_t bytes = rec->packer->packed_bytes(outcount);
+  const int64_t bytes = irr ? irr->packed_bytes(outcount) : rec->packer->packed_bytes(outcount);
   if (*position < 0 || int64_t(*position) + bytes > int64_t(insize))
     return raise_error(comm, MPI_ERR_TRUNCATE);
-  char *origin = static_cast<char *>(dst.dptr) - rec->desc.start;
+  char *origin = static_cast<char *>(dst.dptr) - start;
   // packed bytes in pageable host memory: copied into a pinned, mapped slab
   // on the host, scattered from there by the kernel (the ONESHOT receive)
   Slab *stage = src.device_accessible ? nullptr : pinned_pool().get(size_t(std::max<int64_t>(bytes, 1)), dst.device);
@@ -480,6 +494,7 @@ int unpack(const void *inbuf, int insize, int *position, void *outbuf, int outco
   const int e = env.faultPack ? 1 : on_device(dst.device, false, !dst.host_accessible,
                                               [&](void *s, Packer::Completion *done) {
     const void *in = stage ? stage->dev : src.dptr;
+    if (irr) return done ? irr->unpack_ticket(origin, in, outcount, s, done) : irr->unpack_async(origin, in, outcount, s);
     return done ? rec->packer->unpack_ticket(origin, in, outcount, s, done)
                 : rec->packer->unpack_async(origin, in, outcount, s);
   });
@@ -498,7 +513,7 @@ TEMPI_EXPORT int MPI_Pack(const void *inbuf, int incount, MPI_Datatype datatype,
   TEMPI_MT_ENTRY;
   resolve_next();
   TEMPI_RANGE("MPI_Pack");
-  return tempi::pack(inbuf, incount, datatype, outbuf, outsize, position, comm);
+  return tempi::pack(inbuf, incount, datatype, outbuf, outsize, position, comm, true);
 }
 
 TEMPI_EXPORT int MPI_Unpack(const void *inbuf, int insize, int *position, void *outbuf, int outcount,
@@ -506,5 +521,5 @@ TEMPI_EXPORT int MPI_Unpack(const void *inbuf, int insize, int *position, void *
   TEMPI_MT_ENTRY;
   resolve_next();
   TEMPI_RANGE("MPI_Unpack");
-  return tempi::unpack(inbuf, insize, position, outbuf, outcount, datatype, comm);
+  return tempi::unpack(inbuf, insize, position, outbuf, outcount, datatype, comm, true);
 }

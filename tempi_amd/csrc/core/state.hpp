@@ -27,10 +27,13 @@ void init_after_mpi();
 void finalize_before_mpi();
 
 // TEMPI's MPI_Pack / MPI_Unpack (GPU kernels, or the library with host
-// staging for types that are not strided blocks)
+// staging for types that are not strided blocks). `application`: the call is
+// the application's own MPI_Pack / MPI_Unpack, the only ones the opt-in
+// segment-list packer serves; the transport's internal calls for types it
+// cannot pack stay library-packed
 int pack(const void *inbuf, int incount, MPI_Datatype datatype, void *outbuf, int outsize, int *position,
-         MPI_Comm comm);
+         MPI_Comm comm, bool application = false);
 int unpack(const void *inbuf, int insize, int *position, void *outbuf, int outcount, MPI_Datatype datatype,
-           MPI_Comm comm);
+           MPI_Comm comm, bool application = false);
 
 } // namespace tempi

@@ -1,6 +1,7 @@
 // tempi_amd/csrc/core/type_cache.cpp -- see type_cache.hpp
 #include "type_cache.hpp"
 
+#include "env.hpp"
 #include "log.hpp"
 
 #include <mutex>
@@ -32,7 +33,15 @@ const TypeRecord *type_commit(MPI_Datatype t) {
     rec->flat1ok = rec->packer->flat(1, &rec->flat1);
     LOG_SPEW("type " << t << " -> " << rec->desc.str());
   } else {
-    LOG_DEBUG("type " << t << " is not a strided block; library handles it");
+    // opt-in: flattened only while the feature is on at commit; off, nothing
+    // more is done here than before
+    if (env.irregular && rec->desc.size > 0)
+      rec->irregular = SegPacker::from_type(t, rec->desc.size, rec->desc.extent, env.irregularMaxSegs);
+    if (rec->irregular)
+      LOG_DEBUG("type " << t << " is not a strided block; segment list of " << rec->irregular->table().disp.size()
+                        << " runs");
+    else
+      LOG_DEBUG("type " << t << " is not a strided block; library handles it");
   }
   std::lock_guard<std::mutex> g(mtx);
   auto &slot = cache[t];
@@ -54,7 +63,13 @@ const TypeRecord *type_lookup(MPI_Datatype t) {
 
 void type_release(MPI_Datatype t) {
   std::lock_guard<std::mutex> g(mtx);
-  if (cache.erase(t)) generation++;
+  auto it = cache.find(t);
+  if (it == cache.end()) return;
+  // the device tables go now, while the GPU runtime is certainly up (only
+  // synchronous calls use them, and those have returned: seglist.hpp)
+  if (it->second->irregular) it->second->irregular->release_device();
+  cache.erase(it);
+  generation++;
 }
 
 void types_init() {
@@ -68,6 +83,8 @@ void types_init() {
 
 void types_finalize() {
   std::lock_guard<std::mutex> g(mtx);
+  for (auto &kv : cache)
+    if (kv.second->irregular) kv.second->irregular->release_device();
   cache.clear();
   generation++;
 }

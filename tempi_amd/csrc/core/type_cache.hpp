@@ -5,6 +5,7 @@
 #pragma once
 
 #include "packer.hpp"
+#include "seglist.hpp"
 #include "types.hpp"
 
 #include <mpi.h>
@@ -20,7 +21,11 @@ typedef std::shared_ptr<const TypeRecord> RecordRef;
 
 struct TypeRecord : std::enable_shared_from_this<TypeRecord> {
   StridedBlock desc;
-  std::unique_ptr<Packer> packer; // null when !desc.valid (library handles it)
+  std::unique_ptr<Packer> packer; // null when !desc.valid (no strided form: the transport leaves it to the library)
+  // !desc.valid types flattened into a segment list at commit (only while
+  // TEMPI_IRREGULAR / tempi_irregular_config is on): MPI_Pack / MPI_Unpack use
+  // it; null otherwise, and the library handles the type
+  std::unique_ptr<SegPacker> irregular;
   tempi_hip_desc flat1{};         // one element as a single descriptor
   bool flat1ok = false;
 

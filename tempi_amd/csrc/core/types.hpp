@@ -16,8 +16,11 @@
 //    one more dimension of stride = extent (fixes SURVEY F2);
 //  * 64-bit counts/offsets throughout;
 //  * anything that is not a strided block (irregular indexed, struct with
-//    several types, darray, ...) is marked not-representable and goes to the
-//    library (never a null-packer crash: SURVEY F3).
+//    several types, darray, ...) is marked not-representable here (never a
+//    null-packer crash: SURVEY F3). Such a type goes to the library, unless
+//    the opt-in segment-list packer (seglist.hpp, TEMPI_IRREGULAR) flattened
+//    it at commit: then MPI_Pack / MPI_Unpack gather / scatter it on the GPU,
+//    and only the transport still leaves it to the library.
 #pragma once
 
 #include <mpi.h>

@@ -44,6 +44,7 @@ _COUNTER_FIELDS = [
     "self_matched", "staged_packs", "staged_unpacks", "ticket_waits", "sync_waits",
     "ticket_batches", "persistent_starts", "batches", "gpu_inflight_ns",
     "bytes_ipc", "bytes_ipc_copy", "bytes_oneshot", "bytes_staged", "bytes_device", "bytes_direct",
+    "irregular_packs", "irregular_unpacks",
 ]
 
 
@@ -88,6 +89,10 @@ class MPI:
         I = ctypes.POINTER(ctypes.c_int)
         L.tempi_partition.argtypes = [ctypes.c_int, I, I, I, ctypes.c_int, I, ctypes.c_int, I]
         L.tempi_placement_info.argtypes = [ctypes.POINTER(ctypes.c_int64)]
+        L.tempi_irregular_config.argtypes = [ctypes.c_int, ctypes.c_int64]
+        L.tempi_type_segments.restype = ctypes.c_int64
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        L.tempi_type_segments.argtypes = [ctypes.c_int64, P64, P64, ctypes.c_int64, P64]
         self.initialized = False
 
     # ------------------------------------------------------------- plumbing
@@ -636,6 +641,23 @@ class MPI:
             "lb": info.lb,
             "extent": info.extent,
         }
+
+    def irregular_config(self, on, max_segs=0):
+        """tempi_irregular_config: GPU packing of irregular datatypes on / off
+        for types committed (and MPI_Pack / MPI_Unpack calls made) afterwards;
+        max_segs <= 0 keeps the run cap. Returns the previous on / off state."""
+        return bool(self.L.tempi_irregular_config(1 if on else 0, int(max_segs)))
+
+    def type_segments(self, t):
+        """tempi_type_segments: ([(disp, len), ...] of one element in type-map
+        order, extent), or None when the type has no segment list"""
+        ext = ctypes.c_int64(0)
+        n = self.L.tempi_type_segments(int(t), None, None, 0, ctypes.byref(ext))
+        if n < 0:
+            return None
+        d, ln = (ctypes.c_int64 * max(n, 1))(), (ctypes.c_int64 * max(n, 1))()
+        self.L.tempi_type_segments(int(t), d, ln, n, ctypes.byref(ext))
+        return [(d[i], ln[i]) for i in range(n)], ext.value
 
     def counters(self):
         c = Counters()
